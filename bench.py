@@ -7,7 +7,12 @@ of MultiTrackNPSSMDNMultistreamParametricModel (recipe diffusion config,
 pairs = 30 pairs x 1024 frames of synthetic features.
 GEMMs run on bf16 MFMA with fp32 accumulation; everything else fp32.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result line (and, with
+--dump-outputs DIR, writes what the last timed step returned as DIR/<name>.npy).  --full adds
+every other measurement to the line: the live gate-GEMM roofline, the per-launch census and
+kernel rooflines, the other shapes / models / data-path / synthesis legs and the CPU baselines
+(each can be dropped again with its --no-* flag).
 Multi-GPU: one process per GPU.  Under torch.distributed.run (WORLD_SIZE set) each rank
 runs directly; `python bench.py --gpus N` without it starts torch.distributed.run with N
 ranks itself (before anything touches the GPU) and exits with its status.  RCCL gradient
@@ -81,6 +86,14 @@ def parse():
     ap.add_argument("--pairs", type=int, default=30)
     ap.add_argument("--frames", type=int, default=1024)
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: live gate-GEMM "
+                         "roofline, census and kernel rooflines, the other legs, synthesis RTF "
+                         "and the CPU baselines (the --no-* flags drop single ones again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (loss, grad "
+                         "norm, a fixed sample of the updated parameters and Adam moments) as "
+                         "DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-synth", action="store_true", help="skip the synthesis RTF leg")
     ap.add_argument("--serial", action="store_true",
@@ -109,6 +122,28 @@ def parse():
     ap.add_argument("--cpu-pairs", type=int, default=10)
     ap.add_argument("--cpu-frames", type=int, default=1024)
     return ap.parse_args()
+
+
+DUMP_SAMPLE = 1 << 21  # elements of each flat buffer (parameters, Adam m, v) that are dumped
+DUMP_SEED = 20250321
+
+
+def dump_outputs(path, loss, norm, opt):
+    """What a caller of the timed step holds after its last call, as float32 .npy files: the
+    returned loss and gradient norm, and the state the step updated in place -- the flat
+    parameters and Adam moments, each at the same DUMP_SAMPLE seeded positions (the buffers
+    are 94 MB each).  Inputs, weights and draws are seeded, so two runs with the same
+    arguments dump the same step."""
+    os.makedirs(path, exist_ok=True)
+    n = opt.flat.numel()
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, DUMP_SAMPLE),
+                                                          replace=False))
+    idx = torch.from_numpy(idx).to(opt.flat.device)
+    out = {"loss": loss.detach().reshape(1), "grad_norm": norm.detach().reshape(1),
+           "params_sample": opt.flat.detach()[idx], "adam_m_sample": opt.m.detach()[idx],
+           "adam_v_sample": opt.v.detach()[idx]}
+    for name, t in out.items():
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
 
 
 def gate_gemm_timing(model, P, T, dev, iters=20):
@@ -1133,14 +1168,14 @@ def main():
     frames = P * T * world * args.steps
     value = frames / elapsed
     loss_v, norm_v = loss.item(), norm.item()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, norm, opt)
     if rank != 0:
         if world > 1:
             import torch.distributed as dist
             dist.destroy_process_group()
         return
-    sec, sec_call, flops = gate_gemm_timing(model, P, T, dev)
-    net = model.mgc_model.denoise_fn
-    gbytes = gate_gemm_bytes(P * T, net.C, net.E, 2 if args.precision == "bf16" else 4)
+    full = args.full
     per_gpu = value / world
     step_tf = per_gpu * TRAIN_FLOP_PER_FRAME / 1e12
     peak_tf = PEAK_BF16_TFLOPS if args.precision == "bf16" else 157.3
@@ -1155,9 +1190,13 @@ def main():
                           "committed, not this run)",
         "work": f"{TRAIN_FLOP_PER_FRAME / 1e6:.1f} MFLOP per main-track frame (GEMM / conv / "
                 "LSTM FLOPs of forward + backward, torch.utils.flop_counter on the oracle, "
-                "SURVEY.md section 8(d)) x frames/s per GPU",
-        "gate_gemm_live": _gate_roofline(args, P, T, sec, sec_call, flops, gbytes)}
-    if world == 1 and not args.no_census:
+                "SURVEY.md section 8(d)) x frames/s per GPU"}
+    if full:
+        sec, sec_call, flops = gate_gemm_timing(model, P, T, dev)
+        net = model.mgc_model.denoise_fn
+        gbytes = gate_gemm_bytes(P * T, net.C, net.E, 2 if args.precision == "bf16" else 4)
+        roof["gate_gemm_live"] = _gate_roofline(args, P, T, sec, sec_call, flops, gbytes)
+    if full and world == 1 and not args.no_census:
         agg, serial_ms, alloc = step_census(model, opt, (xm, xs, ym, s0, s1, lens))
         # step-level algorithmic bytes: every tensor the step materialises written once and
         # read once (2 x the bytes the step allocates: activations, saved state, gradients
@@ -1207,23 +1246,30 @@ def main():
         "executed_tflops_per_s": value * (TRAIN_FLOP_PER_FRAME - SUBTRACK_SKIPPED_FLOP) / 1e12,
         "roofline": roof,
     }
-    if world == 1 and not args.no_census:
+    if full and world == 1 and not args.no_census:
         out["census"] = census
-    if not args.no_shapes and world == 1:
+    if full and world == 1:
+        other_legs(args, dev, model, opt, out, value, elapsed)
+    print(json.dumps(out), flush=True)
+
+
+def other_legs(args, dev, model, opt, out, value, elapsed):
+    """--full, one GPU: the legs beside the main line, each under its key of the line."""
+    if not args.no_shapes:
         out["shapes"] = shape_legs(args, dev, model, opt, elapsed / args.steps * 1e3)
-    if not args.no_real_data and world == 1:
+    if not args.no_real_data:
         out["real_data"] = real_data_train(args, dev)
         out["real_data"]["ratio_to_fixed_shape"] = out["real_data"]["value"] / value
-    if not args.no_sf0 and world == 1:
+    if not args.no_sf0:
         out["separate_f0"] = sf0_train(args, dev)
-    if not args.no_config2 and world == 1:
+    if not args.no_config2:
         out["config2"] = config2_train(args, dev)
         out["interaction_loss"] = il_train(args, dev)
-    if not args.no_transformer and world == 1:
+    if not args.no_transformer:
         out["transformer"] = transformer_train(dev)
-    if not args.no_synth and world == 1:
+    if not args.no_synth:
         out["synth"] = synth_rtf(model, dev)
-    if not args.no_cpu_baseline and world == 1:
+    if not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args)
         if "separate_f0" in out:
             out["separate_f0"]["cpu_baseline"] = sf0_cpu_baseline()
@@ -1231,7 +1277,6 @@ def main():
             out["synth"]["cpu_baseline"] = cpu_synth_baseline(out["synth"]["frames"])
         if "transformer" in out:
             out["transformer"]["cpu_baseline"] = transformer_cpu_baseline()
-    print(json.dumps(out), flush=True)
 
 
 def exchange_report(events, opt, model, world, backend, args, step_ms):

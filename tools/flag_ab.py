@@ -27,7 +27,7 @@ for kv in {arm!r}.split(","):
             mod, flag = k.rsplit(".", 1) if "." in k else ("kernels", k)
             getattr(importlib.import_module("ensemble_svs_with_interactions_amd." + mod),
                     flag)[key] = bool(int(v))
-sys.argv = ["bench.py", "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--no-synth",
+sys.argv = ["bench.py", "--full", "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--no-synth",
             "--no-census", "--no-config2", "--no-shapes", "--no-real-data",
             ] + ([] if {tf!r} else ["--no-transformer"]) + ([] if {sf0!r} else ["--no-sf0"])
 import bench

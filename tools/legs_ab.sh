@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.."
 root=$(pwd)
 for rep in 1 2; do
   for d in "$@"; do
-    (cd "$root/$d" && ENSVS_LIB= timeout -k 10 400 python -u bench.py --no-cpu-baseline \
+    (cd "$root/$d" && ENSVS_LIB= timeout -k 10 400 python -u bench.py --full --no-cpu-baseline \
       --no-synth --no-sf0 --no-census --no-transformer 2>/dev/null) | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
