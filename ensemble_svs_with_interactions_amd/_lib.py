@@ -61,6 +61,8 @@ SIGNATURES = {
     "ensvs_conv_wgrad_bf16": [c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                               c_int, c_int, c_int, c_int, c_vp, c_vp, c_ll, c_ll, c_ll, c_int,
                               c_float, c_vp],
+    "ensvs_conv_wgrad_bf16_group": [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                    c_int, c_int, c_int, c_int, c_float, c_vp],
     "ensvs_conv_gemm_bf16a_out": [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
                                   c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_int, c_float,
                                   c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_int, c_vp,

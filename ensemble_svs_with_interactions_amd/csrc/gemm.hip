@@ -3212,6 +3212,25 @@ struct WgradArgs {
   int Tout, M, N, splits, rows_per_split, vecy, vecx;
 };
 
+// The bf16-operand kernels (wgrad_b16_kernel, wgrad_b16_big_kernel) run G problems of one
+// shape in a launch (ensvs_conv_wgrad_bf16_group; a single launch is G = 1): `a` holds what
+// the problems share, the table -- by value in the kernel argument, no device-side copy, so
+// graph capture sees a plain launch -- what differs.
+constexpr int WGRAD_GROUP_MAX = 32;
+struct WgradProb {
+  const __bf16* dy;
+  const __bf16* x;
+  float* part;  // splits > 1: [splits][taps][N][K]
+  float* dst;   // splits == 1: dst[n*sn + k*sk + j*sj]
+  long long sn, sk, sj;
+  int dil, shift0;
+};
+struct WgradGroup {
+  WgradArgs a;  // dy, x, part, dst, sn, sk, sj, dil, shift0 unused: per problem below
+  WgradProb p[WGRAD_GROUP_MAX];
+};
+static_assert(sizeof(WgradGroup) <= 3584, "kernel argument size");
+
 // bf16 staging image of one operand: [BK frames][128 channels], 256-B rows whose 16-B
 // chunks are XOR-swizzled so the transposed MFMA-operand reads (ds_read_b64_tr_b16)
 // and the row writes are bank-conflict free (cdna_hip_programming.md T10, image (b)).
@@ -3262,6 +3281,29 @@ __device__ __forceinline__ void wgrad_tile(const WgradArgs& a, int& n0, int& k0,
   const int t = w - j * gx * gy;
   k0 = (t / gx) * BN;
   n0 = (t % gx) * BM;
+}
+
+// The map of a grouped launch (gridDim.z = problems x splits x taps): the same XCD-contiguous
+// ranges over the problem-major (problem, split, tap, K tile, N tile) order, so the workgroups
+// of one (problem, split) still share an L2, and inside a problem the (split, tap, tile) of a
+// workgroup index is what wgrad_tile gives a single launch.  TN x TK: the output tile.
+template <int TN, int TK>
+__device__ __forceinline__ void wgrad_tile_group(const WgradArgs& a, int& p, int& n0, int& k0,
+                                                 int& j, int& s) {
+  const int gx = gridDim.x, gy = gridDim.y;
+  const int b = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
+  const int total = gx * gy * gridDim.z;
+  const int q = total >> 3, r = total & 7, x = b & 7;
+  int idx = x * q + min(x, r) + (b >> 3);
+  const int W = gx * gy * a.taps;  // workgroups per split
+  p = idx / (W * a.splits);
+  idx -= p * W * a.splits;
+  s = idx / W;
+  const int w = idx - s * W;
+  j = w / (gx * gy);
+  const int t = w - j * gx * gy;
+  k0 = (t / gx) * TK;
+  n0 = (t % gx) * TN;
 }
 
 template <typename T, bool VEC>
@@ -3618,18 +3660,21 @@ __device__ __forceinline__ void wait_chunks(int ahead) {
   }
 }
 
-__global__ __launch_bounds__(NTHR) void wgrad_b16_kernel(const WgradArgs a) {
+__global__ __launch_bounds__(NTHR) void wgrad_b16_kernel(const WgradGroup g) {
+  const WgradArgs& a = g.a;
   constexpr int IMG = BK * 256;  // bytes per operand image (32 frames x 128 channels bf16)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wid >> 1, wc = wid & 1;
-  int n0, k0, j, s;
-  wgrad_tile(a, n0, k0, j, s);
+  int pi, n0, k0, j, s;
+  wgrad_tile_group<BM, BN>(a, pi, n0, k0, j, s);
+  const WgradProb& pr = g.p[pi];
   const int mbeg = s * a.rows_per_split;
   const int mend = min(a.M, mbeg + a.rows_per_split);
   const int nch = mbeg < mend ? (mend - mbeg + BK - 1) / BK : 0;
-  const __bf16* dy = (const __bf16*)a.dy;
-  const __bf16* x = (const __bf16*)a.x;
+  const __bf16* dy = pr.dy;
+  const __bf16* x = pr.x;
+  const int tap0 = pr.shift0 + j * pr.dil;  // this tap's source-frame offset
   unsigned long long zpu = (unsigned long long)(const void*)g_zero;
   asm volatile("" : "+s"(zpu));
   const char* zp = (const char*)zpu;
@@ -3654,7 +3699,7 @@ __global__ __launch_bounds__(NTHR) void wgrad_b16_kernel(const WgradArgs a) {
       const int n = n0 + cc[i] * 8, k = k0 + cc[i] * 8;
       const void* ga = (mv && n < a.N) ? (const void*)(dy + (long long)m * a.ldy + n)
                                        : (const void*)zp;
-      const int src = pad_src(ft[i] + a.shift0 + j * a.dil, a.Tin, a.pad);
+      const int src = pad_src(ft[i] + tap0, a.Tin, a.pad);
       const void* gb = (mv && src >= 0 && k < a.K)
                            ? (const void*)(x + (long long)(fb[i] * a.Tin + src) * a.ldx + k)
                            : (const void*)zp;
@@ -3722,7 +3767,7 @@ __global__ __launch_bounds__(NTHR) void wgrad_b16_kernel(const WgradArgs a) {
         for (int r = 0; r < 4; ++r) {
           const int n = n0 + wr * 64 + mt * 16 + (lane >> 4) * 4 + r;
           if (n < a.N) {
-            float* d = a.dst + n * a.sn + k * a.sk + j * a.sj;
+            float* d = pr.dst + n * pr.sn + k * pr.sk + j * pr.sj;
             const float v = acc[mt][nt][r] * a.scale;
             *d = a.accum ? *d + v : v;
           }
@@ -3730,7 +3775,7 @@ __global__ __launch_bounds__(NTHR) void wgrad_b16_kernel(const WgradArgs a) {
     }
     return;
   }
-  float* out = a.part + ((long long)(s * a.taps + j) * a.N) * a.K;
+  float* out = pr.part + ((long long)(s * a.taps + j) * a.N) * a.K;
 #pragma unroll
   for (int nt = 0; nt < 4; ++nt) {
     const int k = k0 + wc * 64 + nt * 16 + (lane & 15);
@@ -3755,35 +3800,22 @@ __global__ __launch_bounds__(NTHR) void wgrad_b16_kernel(const WgradArgs a) {
 // Staging: the chunk's four [32 frames][128 channels] sub-images (dy lo / hi, x lo / hi, with
 // wg_off's swizzle); wave w moves rows 4w .. 4w + 3 of each (one 1-KB DMA per sub-image).
 constexpr int WGB = 256, NTHRW = 512;
-__device__ __forceinline__ void wgrad_tile_big(const WgradArgs& a, int& n0, int& k0, int& j,
-                                               int& s) {
-  const int gx = gridDim.x, gy = gridDim.y;
-  const int b = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-  const int total = gx * gy * gridDim.z;
-  const int q = total >> 3, r = total & 7, x = b & 7;
-  const int idx = x * q + min(x, r) + (b >> 3);  // XCD-contiguous, as wgrad_tile
-  const int W = gx * gy * a.taps;
-  s = idx / W;
-  const int w = idx - s * W;
-  j = w / (gx * gy);
-  const int t = w - j * gx * gy;
-  k0 = (t / gx) * WGB;
-  n0 = (t % gx) * WGB;
-}
-
-__global__ __launch_bounds__(NTHRW) void wgrad_b16_big_kernel(const WgradArgs a) {
+__global__ __launch_bounds__(NTHRW) void wgrad_b16_big_kernel(const WgradGroup g) {
+  const WgradArgs& a = g.a;
   constexpr int IMG = BK * 256;  // one sub-image: 32 frames x 128 channels bf16
   constexpr int STG = 4 * IMG;   // dy lo, dy hi, x lo, x hi
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wid >> 2, wc = wid & 3;
-  int n0, k0, j, s;
-  wgrad_tile_big(a, n0, k0, j, s);
+  int pi, n0, k0, j, s;
+  wgrad_tile_group<WGB, WGB>(a, pi, n0, k0, j, s);
+  const WgradProb& pr = g.p[pi];
   const int mbeg = s * a.rows_per_split;
   const int mend = min(a.M, mbeg + a.rows_per_split);
   const int nch = mbeg < mend ? (mend - mbeg + BK - 1) / BK : 0;
-  const __bf16* dy = (const __bf16*)a.dy;
-  const __bf16* x = (const __bf16*)a.x;
+  const __bf16* dy = pr.dy;
+  const __bf16* x = pr.x;
+  const int tap0 = pr.shift0 + j * pr.dil;  // this tap's source-frame offset
   unsigned long long zpu = (unsigned long long)(const void*)g_zero;
   asm volatile("" : "+s"(zpu));
   const char* zp = (const char*)zpu;
@@ -3794,7 +3826,7 @@ __global__ __launch_bounds__(NTHRW) void wgrad_b16_big_kernel(const WgradArgs a)
     char* base = smem + (ch % WNS) * STG + (wid * 4) * 256;
     const int m = mbeg + ch * BK + fr;
     const bool mv = m < mend;
-    const int src = pad_src(ft + a.shift0 + j * a.dil, a.Tin, a.pad);
+    const int src = pad_src(ft + tap0, a.Tin, a.pad);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int n = n0 + h * 128 + cc * 8, k = k0 + h * 128 + cc * 8;
@@ -3859,7 +3891,7 @@ __global__ __launch_bounds__(NTHRW) void wgrad_b16_big_kernel(const WgradArgs a)
         acc[i][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fbv[q], acc[i][q], 0, 0, 0);
     }
   }
-  float* out = a.splits == 1 ? nullptr : a.part + ((long long)(s * a.taps + j) * a.N) * a.K;
+  float* out = a.splits == 1 ? nullptr : pr.part + ((long long)(s * a.taps + j) * a.N) * a.K;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int k = k0 + wc * 64 + q * 16 + (lane & 15);
@@ -3873,7 +3905,7 @@ __global__ __launch_bounds__(NTHRW) void wgrad_b16_big_kernel(const WgradArgs a)
         if (out) {
           out[(long long)n * a.K + k] = acc[i][q][r];
         } else {
-          float* d = a.dst + n * a.sn + k * a.sk + j * a.sj;
+          float* d = pr.dst + n * pr.sn + k * pr.sk + j * pr.sj;
           const float v = acc[i][q][r] * a.scale;
           *d = a.accum ? *d + v : v;
         }
@@ -4516,8 +4548,10 @@ static int g_wgrad_big = 1;
 // conditioner (N = 10 240: 296 -> 231 us) and skip projection (K = 5 120: 131 -> 118 us):
 // with one workgroup per CU its chunks ran 1.8 us apart, twice the 128 x 128 kernel's per-CU
 // byte rate lost to the barrier of one 8-wave workgroup (profiles/r4_wgrad_big_bench.txt).
-static bool wgrad_big_shape(int N, int K, int taps) {
-  return g_wgrad_big && N >= WGB && K >= WGB && (long long)cdiv(N, WGB) * cdiv(K, WGB) * taps >= 16;
+// A grouped launch (G problems, ensvs_conv_wgrad_bf16_group) counts the tiles of all of them.
+static bool wgrad_big_shape(int N, int K, int taps, int G = 1) {
+  return g_wgrad_big && N >= WGB && K >= WGB &&
+         (long long)cdiv(N, WGB) * cdiv(K, WGB) * taps * G >= 16;
 }
 // split-K fills about this many workgroups (only when the caller passes a workspace)
 static const int SPLITK_TARGET = 256;
@@ -5119,30 +5153,23 @@ ENSVS_API int ensvs_conv_wgrad(const float* dy, int ldy, const float* x, int ldx
 }
 
 
-// Weight gradient with bf16 operands (dy, x rounded to bf16 in HBM; radd folded into x).
-ENSVS_API int ensvs_conv_wgrad_bf16(const void* dy, int ldy, const void* x, int ldx, int B,
-                                    int Tout, int Tin, int N, int K, int taps, int dil, int shift0,
-                                    int pad, int splits, float* part, float* dst, long long sn,
-                                    long long sk, long long sj, int accum, float scale,
-                                    void* stream) {
-  const int defer = accum;  // ENSVS_WGRAD_DEFER: partials only
-  accum &= 1;
+static_assert(WGRAD_GROUP_MAX <= WRED_BATCH, "one reduce launch per grouped launch");
+
+// One launch of the bf16-operand kernels over m <= 32 problems of one shape (`of`: the
+// problems of the whole list, which picks the kernel).
+static int wgrad_b16_launch(const ensvs_wgrad_prob* probs, int m, int of, int ldy, int ldx, int B,
+                            int Tout, int Tin, int N, int K, int taps, int pad, int splits,
+                            int accum, float scale, hipStream_t st) {
   if (B <= 0 || Tout <= 0 || N <= 0 || K <= 0 || taps <= 0 || splits <= 0) return ENSVS_E_SHAPE;
   // K (N) % 8 != 0: the last 16-B chunk of an x (dy) row reads up to K (N) rounded to 8, the
   // caller's zero padding (stores check k < K, n < N)
-  if (ldy % 8 || ldy < (N + 7) / 8 * 8 || ldx % 8 || ldx < (K + 7) / 8 * 8 ||
-      (((uintptr_t)dy | (uintptr_t)x) & 15))
-    return ENSVS_E_ARG;
-  WgradArgs a{};
-  a.dy = (const float*)dy;
-  a.x = (const float*)x;
-  a.part = part;
+  if (ldy % 8 || ldy < (N + 7) / 8 * 8 || ldx % 8 || ldx < (K + 7) / 8 * 8) return ENSVS_E_ARG;
+  WgradGroup g{};
+  WgradArgs& a = g.a;
   a.ldy = ldy;
   a.ldx = ldx;
   a.K = K;
   a.taps = taps;
-  a.dil = dil;
-  a.shift0 = shift0;
   a.pad = pad;
   a.Tin = Tin;
   a.Tout = Tout;
@@ -5150,30 +5177,79 @@ ENSVS_API int ensvs_conv_wgrad_bf16(const void* dy, int ldy, const void* x, int 
   a.N = N;
   a.splits = splits;
   a.rows_per_split = (cdiv(a.M, splits) + BK - 1) / BK * BK;
-  a.dst = dst;
-  a.sn = sn;
-  a.sk = sk;
-  a.sj = sj;
   a.scale = scale;
   a.accum = accum;
-  if (N * taps > 65535) return ENSVS_E_SHAPE;
-  hipStream_t st = (hipStream_t)stream;
-  if (wgrad_big_shape(N, K, taps)) {
+  for (int i = 0; i < m; ++i) {
+    const ensvs_wgrad_prob& p = probs[i];
+    if (!p.dy || !p.x || (((uintptr_t)p.dy | (uintptr_t)p.x) & 15) ||
+        (splits > 1 ? !p.part : !p.dst))
+      return ENSVS_E_ARG;
+    g.p[i] = WgradProb{(const __bf16*)p.dy, (const __bf16*)p.x, p.part, p.dst, p.sn, p.sk, p.sj,
+                       p.dil, p.shift0};
+  }
+  if (N * taps > 65535 || (long long)taps * splits * m > 65535) return ENSVS_E_SHAPE;
+  if (wgrad_big_shape(N, K, taps, of)) {
     const size_t lds = WNS * 4 * BK * 256;
     static const hipError_t e = hipFuncSetAttribute(
         (const void*)wgrad_b16_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return ENSVS_E_HIP;
-    hipLaunchKernelGGL(wgrad_b16_big_kernel, dim3(cdiv(N, WGB), cdiv(K, WGB), taps * splits),
-                       dim3(NTHRW), lds, st, a);
+    hipLaunchKernelGGL(wgrad_b16_big_kernel, dim3(cdiv(N, WGB), cdiv(K, WGB), taps * splits * m),
+                       dim3(NTHRW), lds, st, g);
   } else {
-    dim3 grid(cdiv(N, BM), cdiv(K, BN), taps * splits);
-    hipLaunchKernelGGL(wgrad_b16_kernel, grid, dim3(NTHR), WNS * 2 * BK * 256, st, a);
+    dim3 grid(cdiv(N, BM), cdiv(K, BN), taps * splits * m);
+    hipLaunchKernelGGL(wgrad_b16_kernel, grid, dim3(NTHR), WNS * 2 * BK * 256, st, g);
   }
   ENSVS_CHECK_LAUNCH();
+  return ENSVS_OK;
+}
+
+// Weight gradient with bf16 operands (dy, x rounded to bf16 in HBM; radd folded into x).
+ENSVS_API int ensvs_conv_wgrad_bf16(const void* dy, int ldy, const void* x, int ldx, int B,
+                                    int Tout, int Tin, int N, int K, int taps, int dil, int shift0,
+                                    int pad, int splits, float* part, float* dst, long long sn,
+                                    long long sk, long long sj, int accum, float scale,
+                                    void* stream) {
+  const ensvs_wgrad_prob p{dy, x, part, dst, sn, sk, sj, dil, shift0};
+  const int defer = accum;  // ENSVS_WGRAD_DEFER: partials only
+  const int rc = wgrad_b16_launch(&p, 1, 1, ldy, ldx, B, Tout, Tin, N, K, taps, pad, splits,
+                                  accum & 1, scale, (hipStream_t)stream);
+  if (rc != ENSVS_OK) return rc;
   if (splits > 1 && !(defer & ENSVS_WGRAD_DEFER)) {
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)cdiv_ll((long long)N * taps * K, 256)),
-                       dim3(256), 0, st, part, dst, splits, taps, N, K, sn, sk, sj, accum, scale);
+                       dim3(256), 0, (hipStream_t)stream, part, dst, splits, taps, N, K, sn, sk,
+                       sj, accum & 1, scale);
     ENSVS_CHECK_LAUNCH();
+  }
+  return ENSVS_OK;
+}
+
+// G weight gradients of one shape in ceil(G / 32) launches: problem-major workgroup order, per
+// problem the workgroups, chunk sequence and sums of its single launch with the same split
+// count -- the same bits.  The kernel is chosen for the whole list's tile count.
+ENSVS_API int ensvs_conv_wgrad_bf16_group(const ensvs_wgrad_prob* probs, int nprob, int ldy,
+                                          int ldx, int B, int Tout, int Tin, int N, int K,
+                                          int taps, int pad, int splits, int accum, float scale,
+                                          void* stream) {
+  const int defer = accum;  // ENSVS_WGRAD_DEFER: partials only
+  accum &= 1;
+  if (nprob < 1 || !probs) return ENSVS_E_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  for (int i0 = 0; i0 < nprob; i0 += WGRAD_GROUP_MAX) {
+    const int m = std::min(WGRAD_GROUP_MAX, nprob - i0);
+    const int rc = wgrad_b16_launch(probs + i0, m, nprob, ldy, ldx, B, Tout, Tin, N, K, taps, pad,
+                                    splits, accum, scale, st);
+    if (rc != ENSVS_OK) return rc;
+    if (splits > 1 && !(defer & ENSVS_WGRAD_DEFER)) {
+      WredBatch b{};
+      for (int i = 0; i < m; ++i) {
+        const ensvs_wgrad_prob& p = probs[i0 + i];
+        b.d[i] = ensvs_wred_desc{p.part, p.dst, p.sn, p.sk, p.sj, splits, taps, N, K, accum, scale};
+      }
+      hipLaunchKernelGGL(wgrad_reduce_batch_kernel,
+                         dim3((unsigned)cdiv_ll((long long)N * taps * K, 256), m), dim3(256), 0,
+                         st, b);
+      ENSVS_CHECK_LAUNCH();
+    }
   }
   return ENSVS_OK;
 }

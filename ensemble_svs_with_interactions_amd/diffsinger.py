@@ -324,6 +324,8 @@ class DiffNet(nn.Module):
         dx = dxb = None
         later = []
         bw = b16 and len(st["XB"]) == L  # bf16 operands saved by the forward
+        grp = bw and K.WGRAD_GROUP["on"]  # per-block weight gradients in grouped launches
+        res_p, dil_p = [], []
         zsrc = st["ZB"] if bw else st["Z"]
         ldz = L * C
         dpre_all = empty(M, L * 2 * C, device=dev)
@@ -369,14 +371,20 @@ class DiffNet(nn.Module):
             # every block (skip half of w_o, conditioner, diffusion projection) and all
             # bias gradients are taken for all blocks at once after the loop
             w_o = blk.output_projection
-            if dx is not None:
+            if grp:
+                # bf16 operands: recorded, issued below as grouped launches
+                if dx is not None:
+                    res_p.append(_wgrad_problem(w_o.weight, dxb, zsrc[l]))
+                dil_p.append(_wgrad_problem(blk.dilated_conv.weight, dpre_b, st["XB"][l],
+                                            dyoff=l * 2 * C, dil=dl, shift0=-dl))
+            elif dx is not None:
                 later.append(lambda w=w_o.weight, g=(dxb if bw else dx), z=zsrc[l]:
                              wg(w, g, C, z, ldz, B, T, T, C, C, scale=SQRT1_2, row0=0))
-            if bw:
+            if bw and not grp:
                 later.append(lambda w=blk.dilated_conv.weight, x_=st["XB"][l], dl=dl, l=l:
                              wg(w, dpre_b, L * 2 * C, x_, C, B, T, T, 2 * C, C, taps=3,
                                 dil=dl, shift0=-dl, dyoff=l * 2 * C))
-            else:
+            elif not bw:
                 later.append(lambda w=blk.dilated_conv.weight, x_=st["X"][l], dl=dl, l=l:
                              wg(w, dpre_all, L * 2 * C, x_, C, B, T, T, 2 * C, C, taps=3,
                                 dil=dl, shift0=-dl, radd=st["ds"][:, l * C:], radd_ld=L * C,
@@ -405,6 +413,14 @@ class DiffNet(nn.Module):
         # 22.9 vs 17.5 ms (round 3, tools/step_ab.py; round 2: 24.8 vs 21.4)
         for f in later:
             f()
+        if grp:
+            n = K.WGRAD_GROUP["blocks"] or L
+            for i in range(0, len(dil_p), n):
+                K.wgrad_group(dil_p[i:i + n], L * 2 * C, C, B, T, T, 2 * C, C, 3, _lib.PAD_ZERO,
+                              accum=True, defer=True)
+            for i in range(0, len(res_p), n):
+                K.wgrad_group(res_p[i:i + n], C, ldz, B, T, T, C, C, 1, _lib.PAD_ZERO,
+                              accum=True, scale=SQRT1_2, defer=True)
         self._bwd_param_tail(st, dout, dx, dss, dssb, tmp_dss, dpre_all, dpre_b, dd_all,
                              dd_tiles, pre_tiles, fuse, bw, b16)
         if after_params is not None:
@@ -497,6 +513,14 @@ class DiffNet(nn.Module):
     def forward(self, spec, diffusion_step, cond):
         """spec (B, 1, M, T), diffusion_step (B,), cond (B, E, T) -> (B, 1, M, T)."""
         return torch_ops.diffnet_call(self, spec, diffusion_step, cond)
+
+
+def _wgrad_problem(param, dy, x, dyoff=0, dil=1, shift0=0):
+    """One problem of kernels.wgrad_group: param.grad += dy^T x, the destination strides of
+    layers.wgrad_into for a Linear (N, K) or Conv1d (N, K, taps) weight."""
+    g = grad_of(param)
+    sn, sk = (g.shape[1], 1) if g.dim() == 2 else (g.shape[1] * g.shape[2], g.shape[2])
+    return dict(dy=dy, x=x, dst=g, sn=sn, sk=sk, sj=1, dyoff=dyoff, dil=dil, shift0=shift0)
 
 
 def _const_step(dsts):

@@ -518,6 +518,27 @@ def flush_wgrad():
     # allocation on this stream reuses them only after the reduction has read them
 
 
+def wgrad_splits(M, N, K, taps, dtype=_lib.DT_BF16):
+    """The row splits one weight-gradient launch takes (wgrad; wgrad_group per problem)."""
+    if (dtype == _lib.DT_BF16 and WGRAD_BIG["on"] and N >= 256 and K >= 256 and
+            -(-N // 256) * -(-K // 256) * taps >= 16):
+        # the 256 x 256-tile kernel (gemm.hip wgrad_b16_big_kernel) for bf16 operands, one
+        # workgroup per CU; fp32 sources rounded in staging (production precision) take the
+        # same split count, so they give the same bits.  Exact-fp32 parity mode (DT_F32)
+        # keeps the 128 x 128 kernel's split rule.
+        tiles = -(-N // 256) * -(-K // 256) * taps
+        return max(1, min(64, WGRAD_BIG["target"] // max(tiles, 1), -(-M // 512)))
+    tiles = -(-N // 128) * -(-K // 128) * taps
+    splits = max(1, min(64, WGRAD_TARGET // max(tiles, 1), -(-M // 256)))
+    # a multiple of 8 lets each split's workgroups share one XCD's L2 (gemm.hip
+    # wgrad_tile) -- when that still fits one wave of WGRAD_TARGET workgroups: rounding
+    # the DiffNet dilated conv's 21 splits up to 24 (576 workgroups) cost 51 -> 68 us
+    up = -(-splits // 8) * 8
+    if splits >= 8 and up * tiles <= WGRAD_TARGET:
+        splits = up
+    return splits
+
+
 def wgrad(dy, ldy, x, ldx, B, Tout, Tin, N, K, taps, dil, shift0, pad, dst, sn, sk, sj,
           accum=False, dtype=_lib.DT_BF16, radd=None, radd_ld=0, dyoff=0, xoff=0, splits=None,
           scale=1.0, dstoff=0, defer=False):
@@ -525,23 +546,8 @@ def wgrad(dy, ldy, x, ldx, B, Tout, Tin, N, K, taps, dil, shift0, pad, dst, sn, 
     tensors already rounded (radd then folded into x): the glds-staged kernel, same bits.
     defer: inside deferred_wgrad(), queue the split reduction (see flush_wgrad)."""
     M = B * Tout
-    if (splits is None and dtype == _lib.DT_BF16 and WGRAD_BIG["on"] and N >= 256 and
-            K >= 256 and -(-N // 256) * -(-K // 256) * taps >= 16):
-        # the 256 x 256-tile kernel (gemm.hip wgrad_b16_big_kernel) for bf16 operands, one
-        # workgroup per CU; fp32 sources rounded in staging (production precision) take the
-        # same split count, so they give the same bits.  Exact-fp32 parity mode (DT_F32)
-        # keeps the 128 x 128 kernel's split rule.
-        tiles = -(-N // 256) * -(-K // 256) * taps
-        splits = max(1, min(64, WGRAD_BIG["target"] // max(tiles, 1), -(-M // 512)))
     if splits is None:
-        tiles = -(-N // 128) * -(-K // 128) * taps
-        splits = max(1, min(64, WGRAD_TARGET // max(tiles, 1), -(-M // 256)))
-        # a multiple of 8 lets each split's workgroups share one XCD's L2 (gemm.hip
-        # wgrad_tile) -- when that still fits one wave of WGRAD_TARGET workgroups: rounding
-        # the DiffNet dilated conv's 21 splits up to 24 (576 workgroups) cost 51 -> 68 us
-        up = -(-splits // 8) * 8
-        if splits >= 8 and up * tiles <= WGRAD_TARGET:
-            splits = up
+        splits = wgrad_splits(M, N, K, taps, dtype)
     def castable(t, ld, C, off):  # ensvs_cast_bf16: the padded copy, or 16-B rows
         return C % 8 or (ld % 4 == 0 and (t.data_ptr() + 4 * off) % 16 == 0)
     if (WGRAD_CAST["on"] and dtype == _lib.DT_BF16 and radd is None and (K % 4 or N % 4)
@@ -587,6 +593,88 @@ def wgrad(dy, ldy, x, ldx, B, Tout, Tin, N, K, taps, dil, shift0, pad, dst, sn, 
              part.data_ptr(), dptr, sn, sk, sj, flag, float(scale), dtype, stream())
     if queue is not None:
         _DEFER["pending"].setdefault(stream(), []).append(queue)
+
+
+# The DiffNet's per-block weight gradients (dilated conv, residual half of w_o) as grouped
+# launches of `blocks` blocks each (ensvs_conv_wgrad_bf16_group; 0: all blocks in one), each
+# problem with the row splits of its single launch: the same bits, one launch and one tail
+# per family instead of one per block.  Off: one launch per block and weight.  bf16 operands
+# only.  fewer_splits: the split count from the tiles of the whole group instead (a fraction
+# of the fp32 partials; the weight gradients then differ in the order of their fp32 sums,
+# and a training run drifts from the single launches' as far as bf16 rounding lets it, so it
+# stays off).  Step: off 13.03-13.13, groups of 4 / 5 / 10: 12.86-12.89, all blocks 12.87 /
+# 12.76, fewer_splits 12.49 / 12.43 ms (profiles/wgrad_group_ab.txt).
+WGRAD_GROUP = {"on": True, "blocks": 0, "fewer_splits": False}
+
+
+class WgradProb(ctypes.Structure):  # include/ensvs.h ensvs_wgrad_prob
+    _fields_ = [("dy", ctypes.c_void_p), ("x", ctypes.c_void_p), ("part", ctypes.c_void_p),
+                ("dst", ctypes.c_void_p), ("sn", ctypes.c_longlong), ("sk", ctypes.c_longlong),
+                ("sj", ctypes.c_longlong), ("dil", ctypes.c_int), ("shift0", ctypes.c_int)]
+
+
+WGRAD_GROUP_MAX = 32  # gemm.hip WGRAD_GROUP_MAX: problems per launch
+
+
+def wgrad_group(problems, ldy, ldx, B, Tout, Tin, N, K, taps, pad, accum=False, splits=None,
+                scale=1.0, defer=False):
+    """wgrad for G problems of one shape in one launch per 32 (bf16 operands): problems is a
+    list of dicts with dy, x, dst, sn, sk, sj and optionally dyoff, xoff, dstoff, dil, shift0.
+    Each problem gets the bits of its own wgrad(..., splits=S) for the S used here: wgrad's
+    own split count for one problem (WGRAD_GROUP["fewer_splits"]: for the group's tiles)."""
+    G = len(problems)
+    if G == 0:
+        return
+    if G > WGRAD_GROUP_MAX:
+        for i0 in range(0, G, WGRAD_GROUP_MAX):
+            wgrad_group(problems[i0:i0 + WGRAD_GROUP_MAX], ldy, ldx, B, Tout, Tin, N, K, taps,
+                        pad, accum, splits, scale, defer)
+        return
+    M = B * Tout
+    if splits is None and not WGRAD_GROUP["fewer_splits"]:
+        splits = wgrad_splits(M, N, K, taps)  # what wgrad takes for one problem
+    if splits is None:  # wgrad's rules applied to the tiles of all G problems
+        t256 = -(-N // 256) * -(-K // 256) * taps * G
+        if WGRAD_BIG["on"] and N >= 256 and K >= 256 and t256 >= 16:
+            splits = max(1, min(64, WGRAD_BIG["target"] // t256, -(-M // 512)))
+        else:
+            tiles = -(-N // 128) * -(-K // 128) * taps * G
+            splits = max(1, min(64, WGRAD_TARGET // tiles, -(-M // 256)))
+            up = -(-splits // 8) * 8  # whole splits per XCD, as wgrad
+            if splits >= 8 and up * tiles <= WGRAD_TARGET:
+                splits = up
+    key = stream()
+    queued = defer and DEFER_WGRAD["on"] and splits > 1 and _DEFER["depth"] > 0
+    per = splits * taps * N * K
+    shared = None if queued or splits == 1 else scratch(G * per, problems[0]["dy"].device)
+    arr = (WgradProb * G)()
+    queue = []
+    for i, p in enumerate(problems):
+        dy, x = p["dy"], p["x"]
+        assert dy.dtype == x.dtype == torch.bfloat16
+        dptr = p["dst"].data_ptr() + 4 * p.get("dstoff", 0)
+        sn, sk, sj = p["sn"], p["sk"], p["sj"]
+        part = None
+        if queued:
+            lo = dptr
+            hi = dptr + 4 * ((N - 1) * sn + (K - 1) * sk + (taps - 1) * sj + 1)
+            pend = _DEFER["pending"].get(key, ())
+            if any(a < hi and lo < b for _, _, (a, b) in list(pend) + queue):
+                flush_wgrad()  # one launch's destinations must not overlap
+                if any(a < hi and lo < b for _, _, (a, b) in queue):
+                    raise ValueError("wgrad_group: overlapping destinations in one group")
+            part = torch.empty(per, dtype=torch.float32, device=dy.device)
+            queue.append(((part.data_ptr(), dptr, sn, sk, sj, splits, taps, N, K, int(accum),
+                           float(scale)), part, (lo, hi)))
+        pp = part.data_ptr() if part is not None else (
+            shared.data_ptr() + 4 * i * per if shared is not None else None)
+        arr[i] = WgradProb(dy.data_ptr() + 2 * p.get("dyoff", 0),
+                           x.data_ptr() + 2 * p.get("xoff", 0), pp, dptr, sn, sk, sj,
+                           p.get("dil", 1), p.get("shift0", 0))
+    call("ensvs_conv_wgrad_bf16_group", ctypes.addressof(arr), G, ldy, ldx, B, Tout, Tin, N, K,
+         taps, pad, splits, int(accum) | (2 if queued else 0), float(scale), key)
+    if queue:
+        _DEFER["pending"].setdefault(key, []).extend(queue)
 
 
 _cnt_cache = {}

@@ -181,6 +181,25 @@ int ensvs_conv_wgrad_bf16(const void* dy, int ldy, const void* x, int ldx, int B
                           float* part, float* dst, long long sn, long long sk, long long sj,
                           int accum, float scale, void* stream);
 
+/* ensvs_conv_wgrad_bf16 for nprob problems that share B, Tout, Tin, N, K, taps, pad, ldy, ldx,
+ * the split count, accum and scale, in one launch per 32 problems (`probs`: a HOST array, passed
+ * by value to the kernel).  Per problem: the operands, dil, shift0 and `part` (splits > 1,
+ * splits*taps*N*K floats of its own) or `dst` with sn / sk / sj (splits == 1; with splits > 1
+ * the reduction's destination, unless ENSVS_WGRAD_DEFER).  Every problem gets the bits of its
+ * own ensvs_conv_wgrad_bf16 with the same split count.  The 256 x 256-tile kernel is chosen by
+ * the tile count of all nprob problems. */
+typedef struct {
+  const void* dy;
+  const void* x;
+  float* part;
+  float* dst;
+  long long sn, sk, sj;
+  int dil, shift0;
+} ensvs_wgrad_prob;
+int ensvs_conv_wgrad_bf16_group(const ensvs_wgrad_prob* probs, int nprob, int ldy, int ldx, int B,
+                                int Tout, int Tin, int N, int K, int taps, int pad, int splits,
+                                int accum, float scale, void* stream);
+
 /* Deferred split reductions of ENSVS_WGRAD_DEFER weight gradients, n descriptors (a HOST
  * array, passed by value to the kernels in chunks of 48): dst[n*sn + k*sk + j*sj] (+)= scale *
  * sum over s of part[s][j][n][k], splits summed in order.  The destinations of one call must

@@ -25,8 +25,8 @@ for kv in {arm!r}.split(","):
             import importlib
             k, key = k.split(":") if ":" in k else (k, "on")
             mod, flag = k.rsplit(".", 1) if "." in k else ("kernels", k)
-            getattr(importlib.import_module("ensemble_svs_with_interactions_amd." + mod),
-                    flag)[key] = bool(int(v))
+            d = getattr(importlib.import_module("ensemble_svs_with_interactions_amd." + mod), flag)
+            d[key] = bool(int(v)) if isinstance(d[key], bool) else int(v)  # e.g. WGRAD_GROUP:blocks=10
 sys.argv = ["bench.py", "--full", "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--no-synth",
             "--no-census", "--no-config2", "--no-shapes", "--no-real-data",
             ] + ([] if {tf!r} else ["--no-transformer"]) + ([] if {sf0!r} else ["--no-sf0"])

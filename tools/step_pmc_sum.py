@@ -43,5 +43,9 @@ out["hbm_bytes_per_step"] = out["hbm_read_bytes_per_step"] + out["hbm_write_byte
 top = sorted(fkern, key=lambda k: -(2 * fkern[k] + wkern.get(k, 0.0)))[:15]
 out["top_kernels_mb_per_step"] = {k: round((2 * fkern[k] + wkern.get(k, 0.0)) * 1024 / STEPS
                                            / 1e6, 1) for k in top}
+# the split reductions' share (weight-gradient partial sums and column sums)
+red = [k for k in set(fkern) | set(wkern) if "wgrad_reduce_batch" in k or "colsum" in k]
+out["reduction_mb_per_step"] = {k: round((2 * fkern.get(k, 0.0) + wkern.get(k, 0.0)) * 1024 / STEPS
+                                         / 1e6, 1) for k in sorted(red)}
 json.dump(out, open(sys.argv[3], "w"), indent=1)
 print(json.dumps(out, indent=1))
